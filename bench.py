@@ -127,6 +127,37 @@ def vision_leg(m, cfg, model_name: str, cpu: bool):
     return out
 
 
+DECODE_CALL_MAX = 4096      # steps one cm_bench_decode call takes (the model's token ring)
+
+
+def decode_steps(m, first: int, k: int):
+    """k greedy decode steps from token `first` through cm_bench_decode, in calls of at most DECODE_CALL_MAX steps.
+    Returns (the k token ids, HIP-event milliseconds of the calls summed)."""
+    import numpy as np
+    toks, ms = [], 0.0
+    while k > 0:
+        t, e = m.bench_decode(first, min(k, DECODE_CALL_MAX))
+        toks.append(t); ms += e
+        first, k = int(t[-1]), k - len(t)
+    return np.concatenate(toks), ms
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: each array as out_dir/<name>.npy in float64 (token ids are exact there), at most DUMP_BYTES_MAX in all;
+    an array over its share is replaced by a fixed, seeded sample of its elements (flattened, in index order)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES_MAX // len(arrays) // 8
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def relaunch_under_torchrun(n: int) -> int:
     """`python bench.py --gpus N` (no torchrun): start the N ranks ourselves, one process per GPU."""
     import torch
@@ -175,10 +206,12 @@ def main():
     ap.add_argument("--force-rccl", action="store_true", help="TP=1 with every reduction routed through a 1-rank RCCL communicator "
                     "(CM_DEBUG_FORCE_RCCL): per-call enqueue cost of the collectives, one GPU")
     ap.add_argument("--isq", default=None, help="in-situ weight quantisation (q8_0): a DIFFERENT workload than the bf16 headline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what they returned (the greedy "
+                    "token ids) as DIR/<name>.npy, so that two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
-    if args.tp_inprocess:      # ranks that share a device need one hardware queue per rank stream: before the HIP runtime starts
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
     n = args.gpus
     if n < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -227,7 +260,6 @@ def main():
         have = torch.cuda.device_count() if torch.cuda.is_available() else 0
         emulated = have < tpg
         devs = [0] * tpg if emulated else list(range(tpg))
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
         mk = lambda coll: Model.synthetic(cfg, seed=0, max_seq_len=max(2048, ctx + K + W + 64), max_seqs=1, use_graph=-1 if args.no_graph else 0,
                                           tp_size=tpg, tp_in_process=True, tp_devices=devs, tp_collective=coll, kv_dtype=args.kv)
         tp_fallback = None
@@ -262,7 +294,7 @@ def main():
     m.debug_fill_kv(ctx, seed=1)            # synthetic KV for positions [0, ctx): inputs resident in HBM
     first = 3
     if W > 0:
-        toks, _ = m.bench_decode(first, W)
+        toks, _ = decode_steps(m, first, W)
         first = int(toks[-1])
 
     def barrier():
@@ -276,7 +308,7 @@ def main():
     barrier()
     dev_sync()
     t0 = time.perf_counter()
-    toks, ev_ms = m.bench_decode(first, K)   # enqueues K steps, synchronises on the model's stream
+    toks, ev_ms = decode_steps(m, first, K)  # enqueues K steps, synchronises on the model's stream
     dev_sync()
     barrier()
     dt = time.perf_counter() - t0
@@ -284,6 +316,9 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"tokens": toks})
 
     ms_per_step = dt * 1e3 / K
     value = K / dt

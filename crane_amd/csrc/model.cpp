@@ -1538,9 +1538,12 @@ void Model::prefill_multi(const int32_t* sq, const uint32_t* const* ids, const s
         }
         std::stable_sort(tl.begin(), tl.end(), [](const int2& x, const int2& y) { return x.y < y.y; });     // start_pos = 0: key tiles = qt + 1
         seg_ntiles = (int)tl.size();
-        CM_HIP(hipMemcpy(d_segtab, hs.data(), hs.size() * sizeof(PrefillSegDev), hipMemcpyHostToDevice));
-        CM_HIP(hipMemcpy(d_rowseg, rs.data(), rs.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        CM_HIP(hipMemcpy(d_tiles, tl.data(), tl.size() * sizeof(int2), hipMemcpyHostToDevice));
+        // on this rank's own stream, not the null stream: ranks of a group that share a device may share a hardware queue with
+        // the null stream, and a copy there would wait behind a peer's exchange kernel that waits for this rank
+        CM_HIP(hipMemcpyAsync(d_segtab, hs.data(), hs.size() * sizeof(PrefillSegDev), hipMemcpyHostToDevice, s));
+        CM_HIP(hipMemcpyAsync(d_rowseg, rs.data(), rs.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        CM_HIP(hipMemcpyAsync(d_tiles, tl.data(), tl.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+        CM_HIP(hipStreamSynchronize(s));                // hs / rs / tl are pageable locals
         seg_tables_ok = true;
     }
     CM_HIP(hipMemcpyAsync(d_ids, h_ids, total * sizeof(uint32_t), hipMemcpyHostToDevice, s));

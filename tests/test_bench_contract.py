@@ -59,3 +59,27 @@ def test_committed_bench_line_carries_the_contract_fields():
     assert lw["greedy_equal"] == lw["greedy_checked"] and max(lw["prefill_logit_rel"], lw["decode_logit_rel"]) < 1e-3
     assert p["logit_rel"] >= max(lw["prefill_logit_rel"], lw["decode_logit_rel"])             # the headline figure includes it
     assert line["roofline_step"]["frac"] >= 0.69
+
+
+def test_timed_steps_and_dumped_outputs(tmp_path):
+    """--steps larger than one cm_bench_decode call is split into calls that continue from the last token, and --dump-outputs
+    writes exactly the token ids those steps returned (float64) -- checked with a stand-in for the model."""
+    import numpy as np
+    import bench
+
+    class Stub:
+        calls = []
+
+        def bench_decode(self, first, k):
+            assert 1 <= k <= bench.DECODE_CALL_MAX
+            self.calls.append((first, k))
+            return (first * 7 + np.arange(1, k + 1, dtype=np.uint32)) % 151936, 0.5
+
+    m = Stub()
+    k = 2 * bench.DECODE_CALL_MAX + 5
+    toks, ms = bench.decode_steps(m, 3, k)
+    assert len(toks) == k and ms == 1.5 and [c[1] for c in m.calls] == [bench.DECODE_CALL_MAX, bench.DECODE_CALL_MAX, 5]
+    assert m.calls[1][0] == int(toks[bench.DECODE_CALL_MAX - 1]) and m.calls[2][0] == int(toks[2 * bench.DECODE_CALL_MAX - 1])
+    bench.dump_outputs(str(tmp_path / "out"), {"tokens": toks})
+    got = np.load(tmp_path / "out" / "tokens.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, toks.astype(np.float64))

@@ -1,7 +1,6 @@
 """Two independent handles on ONE device driven from two host threads at once (no tensor parallelism): each must reproduce
 what it computes alone.  (Reproducer for the split-K prompt GEMM under concurrent kernels of another stream.)"""
 import os, sys, threading
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 sys.path.insert(0, ".")
 import numpy as np
 from crane_amd import configs

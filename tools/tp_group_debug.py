@@ -1,7 +1,6 @@
 """GPU-box reproducer for order-dependent failures of tests/test_gpu_tp_group.py: groups created and destroyed in a given order.
    python tools/tp_group_debug.py d2,d4,h2,d2   (d = dense tiny, h = hybrid tiny, digit = tp)"""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 sys.path.insert(0, ".")
 import numpy as np
 from crane_amd import configs
